@@ -21,6 +21,10 @@ of data-path collectives inside the timed region; `objective` is BASELINE.json c
 objective + gradient, one all-reduce of 13 doubles per evaluation), timed by the same rule right after the headline.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+
+`--dump-outputs DIR` writes what the last timed step returned (xi, sigma and the reduced gradient for the headline; at most
+32 MiB, per-point rows at a fixed seeded sample of the points) as DIR/<name>.npy, fp64.  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -193,6 +197,7 @@ def history_workload(args, dev, rank, world, distributed):
     elapsed = float(tmax.item())
     assert np.isfinite(r.J) and np.isfinite(r.grad).all()
     if rank == 0:
+        dumped = write_dump(args.dump_outputs, {"J": np.array([r.J]), "grad": r.grad}) if args.dump_outputs else None
         # one launch per evaluation (cm_objective_grad_history): forward read grad u 32, write xi 64; adjoint read
         # grad u 32 + previous xi 64 + data 48.  --per-step-history (one launch per step and direction): forward read
         # grad u 32 + xi_prev 64, write xi 64; adjoint read grad u 32 + xi_prev 64 + xi 64 + data 48 + history 64,
@@ -208,9 +213,33 @@ def history_workload(args, dev, rank, world, distributed):
             "roofline": {"bound": "hbm", "achieved": bytes_per * B * K * args.steps / elapsed / 1e9, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": bytes_per * B * K * args.steps / elapsed / 1e9 / HBM_PEAK_GBS,
                          "traffic": None, "kernel": "k_history" if fused else "k_update + k_reverse<MODE 2> per history step",
-                         "kernel_ms": elapsed / args.steps * 1e3, "algorithmic_bytes_per_update": bytes_per}}))
+                         "kernel_ms": elapsed / args.steps * 1e3, "algorithmic_bytes_per_update": bytes_per},
+            **({"dump": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {})}))
     if distributed:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 32 << 20            # --dump-outputs: budget of the per-point rows written
+DUMP_SEED = 20240611             # --dump-outputs: seed of the point sample (fixed: two builds dump the same points)
+
+
+def dump_sample(B, rows):
+    """Sorted indices of the points whose per-point rows --dump-outputs writes: all B points when `rows` fp64 rows of them fit
+    in DUMP_BYTES, else a fixed seeded sample of as many as fit."""
+    import numpy as np
+    n = min(B, DUMP_BYTES // (8 * rows))
+    if n == B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+
+
+def write_dump(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, fp64; returns {name: shape} for the JSON line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: list(np.shape(a)) for name, a in arrays.items()}
 
 
 def launcher_command(n_ranks, port, argv):
@@ -293,7 +322,13 @@ def main():
                              "hybrid_update", "hosford_update_vjp", "hybrid_update_vjp", "hosford_update_tangent", "hybrid_update_tangent",
                              "ps_calibration_history", "calibration_history"],
                     help="default = BASELINE.json configs[1]; the others are side measurements (DESIGN.md section 6)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (fp64): "
+                         "the per-point rows (xi, sigma, dsigma) at a fixed seeded sample of the points, reduced results whole; "
+                         "rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # Not started by a launcher (no WORLD_SIZE): N > 1 -- or the 1-rank rehearsal of the process-group path -- runs under
     # torch.distributed.run as child processes, started before anything here imports torch or touches the GPU.
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_launch or os.environ.get("CMAD_BENCH_FORCE_DIST") == "1"):
@@ -492,6 +527,7 @@ def main():
         host_t = [0.0] * (steps + 1)
         if distributed:
             dist.barrier()
+        r = None
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for k in range(steps):
@@ -524,9 +560,24 @@ def main():
                 "start_gaps_ms": [starts[k].elapsed_time(starts[k + 1]) for k in range(steps - 1)],
                 "host_issue_ms": [(host_t[k + 1] - host_t[k]) * 1e3 for k in range(steps)],
                 "per_rank_kernel_ms": per_rank_kernel_ms, "collective_calls": calls[0], "finite": finite,
-                "payload_doubles": 13 if w == "j2_objective_grad" else (12 if w.endswith("_update_vjp") else 0)}
+                "payload_doubles": 13 if w == "j2_objective_grad" else (12 if w.endswith("_update_vjp") else 0),
+                "last": r}                             # the reduced result of the last timed step (None for an update)
 
     tr = timed_region(wl, args.steps, args.warmup)
+    dump, dump_points = None, 0
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step, copied to the host now: the regions below reuse the buffers
+        if wl == "j2_objective_grad":
+            res13 = tr["last"].cpu().numpy()
+            dump = {"J": res13[:1], "grad": res13[1:]}
+        else:
+            rows = {name: out[name] for name in ("xi", "sigma", "dsigma") if name in out}
+            idx = dump_sample(B, sum(t.shape[0] for t in rows.values()))
+            idx_dev = torch.from_numpy(idx).to(dev)
+            dump = {name: t.index_select(1, idx_dev).cpu().numpy() for name, t in rows.items()}
+            if wl.endswith("_update_vjp"):
+                dump["grad"] = tr["last"].cpu().numpy()
+            dump_points = len(idx)
     elapsed, local_elapsed, per_step_ms, kernel_ms = tr["elapsed"], tr["local_elapsed"], tr["per_step_ms"], tr["kernel_ms"]
     device_span_ms, start_gaps_ms, host_issue_ms = tr["device_span_ms"], tr["start_gaps_ms"], tr["host_issue_ms"]
     per_rank_kernel_ms = tr["per_rank_kernel_ms"]
@@ -692,6 +743,11 @@ def main():
             res["with_line_search"] = dict(side(NewtonSettings.traced()), max_evals=4)
         if n == 1 and not args.no_cpu_baseline and wl == "j2_update_vjp" and not args.sustain:
             res["cpu_baseline"] = cpu_baseline(values)
+        if dump is not None:
+            res["dump"] = {"dir": args.dump_outputs, "arrays": write_dump(args.dump_outputs, dump),
+                           "points": ({"sampled": dump_points, "of": B, "seed": DUMP_SEED,
+                                       "rule": "sorted numpy default_rng(seed).choice(of, sampled, replace=False) of rank 0's shard"
+                                       if dump_points < B else "all points of rank 0's shard"} if dump_points else None)}
         print(json.dumps(res))
     if distributed:
         dist.destroy_process_group()
