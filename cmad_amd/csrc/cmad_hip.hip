@@ -1398,7 +1398,7 @@ __global__ __launch_bounds__(64) void k_hessian_weights(cm_model_desc m, int64_t
     W[(ps * NQ + b) * NQ + a] = w;
 }
 
-// ---- second-order pass including EXTENDED parameters (cm_direct_history_ep, cm_hessian_history_ep) -------------------------
+// ---- second-order pass including EXTENDED parameters (cm_direct_history_ep, cm_hessian_history_ep(_block)) ------------------
 // q = [xi_k, xi_{k-1}, p (12 native), pe (n_ep extended)], NQ = 2 NX + 12 + n_ep (run time), D_k = dq/d[p, pe].
 template <int DEF, int YK, bool ROT, int MK>
 __global__ __launch_bounds__(64) void k_direct_history_ep(cm_model_desc m, int64_t B, int K, int n_ep, const int32_t* __restrict__ ep_index,
@@ -1429,21 +1429,28 @@ __global__ __launch_bounds__(64) void k_direct_history_ep(cm_model_desc m, int64
     }
 }
 
+// One rectangular block of W per (point, step): rows over q_I = [xi_k, xi_{k-1}, p, p_I] (NI = 2 NX + 12 + n_row), columns
+// over q_J = [xi_k, xi_{k-1}, p, p_J] (NJ = 2 NX + 12 + n_col), W[ps][NI][NJ] row-major.  ep_cat is ONE index list for
+// cm::hessian_pair, [row leaves, column leaves]: column leaf j is its extended direction col_off + j.  sym (the row and the
+// column list are the same list, col_off = 0): one thread per pair a <= b, mirrored; otherwise one thread per entry.
 template <int DEF, int YK, bool ROT, int MK>
-__global__ __launch_bounds__(64) void k_hessian_weights_ep(cm_model_desc m, int64_t B, int K, int n_ep, const int32_t* __restrict__ ep_index,
-        const double* __restrict__ gradu_hist, const double* __restrict__ xi_hist, const double* __restrict__ lam_hist,
-        const double* __restrict__ sbar_hist, Wsq hss, const double* __restrict__ hss_hist, const double* __restrict__ hxx_hist,
-        double* __restrict__ W) {
-    constexpr int NX = nx_of<DEF, MK>(), NU = Dims<DEF>::NU;
-    const int NQ = 2 * NX + CM_NUM_PARAMS + n_ep, NPAIR = NQ * (NQ + 1) / 2;
+__global__ __launch_bounds__(64) void k_hessian_weights_blk(cm_model_desc m, int64_t B, int K, int n_row, int n_col, int col_off, bool sym,
+        const int32_t* __restrict__ ep_cat, const double* __restrict__ gradu_hist, const double* __restrict__ xi_hist,
+        const double* __restrict__ lam_hist, const double* __restrict__ sbar_hist, Wsq hss, const double* __restrict__ hss_hist,
+        const double* __restrict__ hxx_hist, double* __restrict__ W) {
+    constexpr int NX = nx_of<DEF, MK>(), NU = Dims<DEF>::NU, NS = 2 * NX + CM_NUM_PARAMS;
+    const int NI = NS + n_row, NJ = NS + n_col;
+    const int per = sym ? NI * (NI + 1) / 2 : NI * NJ;
     const int64_t tid = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (tid >= B * K * NPAIR) return;
-    const int64_t ps = tid / NPAIR;
+    if (tid >= B * K * per) return;
+    const int64_t ps = tid / per;
     const int64_t pt = ps % B;
     const int step = (int)(ps / B) + 1;
-    int rem = (int)(tid % NPAIR), a = 0;
-    while (rem >= NQ - a) { rem -= NQ - a; ++a; }
-    const int b = a + rem;
+    int rem = (int)(tid % per), a = 0, b;
+    if (sym) {
+        while (rem >= NI - a) { rem -= NI - a; ++a; }
+        b = a + rem;
+    } else { a = rem / NJ; b = rem % NJ; }
     double G[NU], xp[NX], x[NX], lam[NX], sbar[6], hs[6];
     for (int k = 0; k < NU; ++k) {
         G[k] = gradu_hist[((int64_t)step * NU + k) * B + pt];
@@ -1455,44 +1462,59 @@ __global__ __launch_bounds__(64) void k_hessian_weights_ep(cm_model_desc m, int6
         lam[k] = lam_hist[((int64_t)step * NX + k) * B + pt];
     }
     for (int r = 0; r < 6; ++r) { sbar[r] = sbar_hist[((int64_t)step * 6 + r) * B + pt]; hs[r] = hss_hist ? hss_hist[step * 6 + r] : hss.w[r]; }
-    double w = hessian_weight<DEF, YK, ROT, MK>(m, G, x, xp, lam, sbar, hs, a, b, ep_index);
+    const int qb = b < NS ? b : b + col_off;
+    double w = hessian_weight<DEF, YK, ROT, MK>(m, G, x, xp, lam, sbar, hs, a, qb, ep_cat);
     if (hxx_hist && a == b && a < NX) w += hxx_hist[step * NX + a];
-    W[(ps * NQ + a) * NQ + b] = w;
-    W[(ps * NQ + b) * NQ + a] = w;
+    W[(ps * NI + a) * NJ + b] = w;
+    if (sym) W[(ps * NI + b) * NJ + a] = w;
 }
 
-// part[ps][i][j] = sum_ab D[a][i] W[a][b] D[b][j] over NPT = 12 + n_ep parameter directions; dynamic LDS: W (NQ x NQ), D (NQ x NPT)
+// Structured quadratic form of one block.  With R = 2 NX state rows x = [xi_k, xi_{k-1}], P_I = [p, p_I] (NPI = 12 + n_row) and
+// P_J = [p, p_J] (NPJ = 12 + n_col), D_I = [Dx_I ; Id] and D_J = [Dx_J ; Id], so that
+//     part[ps] = D_I^T W D_J = Dx_I^T (W_xx Dx_J + W_xJ) + W_Ix Dx_J + W_IJ
+// (every row of D below the first R is an identity row).  One block per (point, step); Dx_I, Dx_J, W_xx, W_Ix and
+// T = W_xx Dx_J + W_xJ in dynamic LDS, (R (NPI + 2 NPJ) + NPI R + R^2) doubles <= 46 KB at 64 + 64 leaves (UNIAXIAL_STRESS);
+// W_xJ and W_IJ are read coalesced from global memory.  O(R NPI NPJ + R^2 NPJ) per (point, step).
 template <int NX>
-__global__ __launch_bounds__(256) void k_hessian_quadform_ep(int64_t B, int K, int n_ep, const double* __restrict__ W,
-        const double* __restrict__ dx_dp_hist, const double* __restrict__ dxe_hist, double* __restrict__ part) {
+__global__ __launch_bounds__(256) void k_hessian_qform_blk(int64_t B, int K, int n_row, int n_col, const double* __restrict__ W,
+        const double* __restrict__ dx_dp_hist, const double* __restrict__ dxe_row, const double* __restrict__ dxe_col,
+        double* __restrict__ part) {
     extern __shared__ double sm[];
-    constexpr int NP_ = CM_NUM_PARAMS;
-    const int NPT = NP_ + n_ep, NQ = 2 * NX + NPT;
-    double* sW = sm;
-    double* sD = sm + NQ * NQ;
+    constexpr int NP_ = CM_NUM_PARAMS, R = 2 * NX;
+    const int NPI = NP_ + n_row, NPJ = NP_ + n_col, NJ = R + NPJ;
+    double* sDI = sm;                     // [R][NPI]
+    double* sDJ = sDI + R * NPI;          // [R][NPJ]
+    double* sT = sDJ + R * NPJ;           // [R][NPJ]
+    double* sWIx = sT + R * NPJ;          // [NPI][R]
+    double* sWxx = sWIx + NPI * R;        // [R][R]
     const int64_t ps = blockIdx.x, pt = ps % B;
     const int step = (int)(ps / B) + 1;
-    for (int i = threadIdx.x; i < NQ * NQ; i += 256) sW[i] = W[ps * NQ * NQ + i];
-    for (int i = threadIdx.x; i < NQ * NPT; i += 256) {
-        const int r = i / NPT, j = i % NPT;
-        double v;
-        if (r < 2 * NX) {
-            const int st = (r < NX) ? step : step - 1, rr = (r < NX) ? r : r - NX;
-            v = (j < NP_) ? dx_dp_hist[(((int64_t)st * NX + rr) * NP_ + j) * B + pt]
-                          : dxe_hist[(((int64_t)st * NX + rr) * n_ep + (j - NP_)) * B + pt];
-        } else v = (r - 2 * NX == j) ? 1.0 : 0.0;
-        sD[i] = v;
+    const double* Wp = W + ps * (int64_t)(R + NPI) * NJ;
+    auto dx = [&](const double* dxe, int n, int r, int j) {
+        const int st = (r < NX) ? step : step - 1, rr = (r < NX) ? r : r - NX;
+        return (j < NP_) ? dx_dp_hist[(((int64_t)st * NX + rr) * NP_ + j) * B + pt]
+                         : dxe[(((int64_t)st * NX + rr) * n + (j - NP_)) * B + pt];
+    };
+    for (int i = threadIdx.x; i < R * NPI; i += 256) sDI[i] = dx(dxe_row, n_row, i / NPI, i % NPI);
+    for (int i = threadIdx.x; i < R * NPJ; i += 256) sDJ[i] = dx(dxe_col, n_col, i / NPJ, i % NPJ);
+    for (int i = threadIdx.x; i < NPI * R; i += 256) sWIx[i] = Wp[(int64_t)(R + i / R) * NJ + i % R];
+    for (int i = threadIdx.x; i < R * R; i += 256) sWxx[i] = Wp[(int64_t)(i / R) * NJ + i % R];
+    __syncthreads();
+    for (int o = threadIdx.x; o < R * NPJ; o += 256) {
+        const int a = o / NPJ, j = o % NPJ;
+        double t = Wp[(int64_t)a * NJ + R + j];
+        for (int b = 0; b < R; ++b) t += sWxx[a * R + b] * sDJ[b * NPJ + j];
+        sT[o] = t;
     }
     __syncthreads();
-    for (int o = threadIdx.x; o < NPT * NPT; o += 256) {
-        const int i = o / NPT, j = o % NPT;
-        double acc = 0.0;
-        for (int a = 0; a < NQ; ++a) {
-            double t = 0.0;
-            for (int b = 0; b < NQ; ++b) t += sW[a * NQ + b] * sD[b * NPT + j];
-            acc += sD[a * NPT + i] * t;
+    for (int o = threadIdx.x; o < NPI * NPJ; o += 256) {
+        const int i = o / NPJ, j = o % NPJ;
+        double t1 = 0.0, t2 = 0.0;
+        for (int a = 0; a < R; ++a) {
+            t1 += sDI[a * NPI + i] * sT[a * NPJ + j];
+            t2 += sWIx[i * R + a] * sDJ[a * NPJ + j];
         }
-        part[ps * (NPT * NPT) + o] = acc;
+        part[ps * (int64_t)(NPI * NPJ) + o] = t1 + t2 + Wp[(int64_t)(R + i) * NJ + R + j];
     }
 }
 
@@ -2184,7 +2206,7 @@ int launch_hessian_history(const cm_model_desc* m, int64_t B, int K, const doubl
 
 
 #if CM_HAS_PART(9)
-constexpr int kMaxEp = 64;           // extended parameter directions per second-order pass (dynamic LDS of the quadratic form)
+constexpr int kMaxEp = 64;           // extended parameter directions per launch and side (the tile of the block quadratic form)
 template <int MK>
 int launch_direct_history_ep(const cm_model_desc* m, int64_t B, int K, int n_ep, const int32_t* ep_index, const double* gradu_hist,
                              const double* xi_hist, double* dxe_hist, void* stream) {
@@ -2204,50 +2226,54 @@ int launch_direct_history_ep(const cm_model_desc* m, int64_t B, int K, int n_ep,
     return check_launch();
 }
 
+// One (12 + n_row) x (12 + n_col) block of d2J/d[p, pe]2 (cm_hessian_history_ep_block; cm_hessian_history_ep is its case row list
+// = column list).  need: the caller's workspace contract.  Workspace: W (nps NI NJ), part (nps NPI NPJ), then -- unless the two
+// lists are one (same pointers and count: the weights are then evaluated for a <= b and mirrored) -- the concatenated index list.
 template <int MK>
-int launch_hessian_history_ep(const cm_model_desc* m, int64_t B, int K, int n_ep, const int32_t* ep_index, const double* gradu_hist,
-                              const double* xi_hist, const double* lam_hist, const double* dx_dp_hist, const double* dxe_hist,
-                              const double* sbar_hist, const double* hss6, const double* hss_hist, const double* hxx_hist,
-                              double* out, void* workspace, int64_t wbytes, void* stream) {
-    if (!m || B < 0 || K < 1 || n_ep < 0 || n_ep > kMaxEp || !out || !workspace || (!hss6 && !hss_hist)) return CM_ERR_BAD_ARG;
+int launch_hessian_block(const cm_model_desc* m, int64_t B, int K, int n_row, const int32_t* row_ep, int n_col, const int32_t* col_ep,
+                         const double* gradu_hist, const double* xi_hist, const double* lam_hist, const double* dx_dp_hist,
+                         const double* dxe_row, const double* dxe_col, const double* sbar_hist, const double* hss6, const double* hss_hist,
+                         const double* hxx_hist, double* out, void* workspace, int64_t wbytes, int64_t need, void* stream) {
+    if (!m || B < 0 || K < 1 || n_row < 0 || n_row > kMaxEp || n_col < 0 || n_col > kMaxEp || !out || !workspace || (!hss6 && !hss_hist))
+        return CM_ERR_BAD_ARG;
     if (!supported(m, MK) || rate_dense(m, MK) || (MK == CM_SMALL_RATE_ELASTIC_PLASTIC && m->def_type == CM_UNIAXIAL_STRESS)) return CM_ERR_UNSUPPORTED;
-    if (B > 0 && (!gradu_hist || !xi_hist || !lam_hist || !dx_dp_hist || !sbar_hist || (n_ep > 0 && (!ep_index || !dxe_hist)))) return CM_ERR_BAD_ARG;
-    if (wbytes < cm_hessian_ep_workspace_bytes(m, B, K, n_ep)) return CM_ERR_WORKSPACE;
-    const int nx = cm_num_xi(m), npt = CM_NUM_PARAMS + n_ep, nq = 2 * nx + npt;
+    if (B > 0 && (!gradu_hist || !xi_hist || !lam_hist || !dx_dp_hist || !sbar_hist || (n_row > 0 && (!row_ep || !dxe_row)) ||
+                  (n_col > 0 && (!col_ep || !dxe_col))))
+        return CM_ERR_BAD_ARG;
+    if (need < 0) return (int)need;
+    if (wbytes < need) return CM_ERR_WORKSPACE;
+    const int nx = cm_num_xi(m), npi = CM_NUM_PARAMS + n_row, npj = CM_NUM_PARAMS + n_col, ni = 2 * nx + npi, nj = 2 * nx + npj;
+    const bool sym = n_row == n_col && row_ep == col_ep && dxe_row == dxe_col;
     const int64_t nps = B * (int64_t)K;
     double* W = (double*)workspace;
-    double* part = W + nps * nq * nq;
+    double* part = W + nps * ni * nj;
     Wsq h; for (int k = 0; k < 6; ++k) h.w[k] = hss6 ? hss6[k] : 0.0;
     const cm_model_desc md = *m;
     (void)hipGetLastError();
     hipStream_t s = (hipStream_t)stream;
     if (nps > 0) {
-        const int64_t nthreads = nps * (int64_t)(nq * (nq + 1) / 2);
+        const int32_t* ep_cat = row_ep;
+        if (!sym) {
+            int32_t* cat = (int32_t*)(part + nps * npi * npj);
+            if (n_row > 0 && hipMemcpyAsync(cat, row_ep, n_row * sizeof(int32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) return CM_ERR_LAUNCH;
+            if (n_col > 0 && hipMemcpyAsync(cat + n_row, col_ep, n_col * sizeof(int32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) return CM_ERR_LAUNCH;
+            ep_cat = cat;
+        }
+        const int64_t nthreads = nps * (int64_t)(sym ? ni * (ni + 1) / 2 : ni * nj);
         const dim3 grid((unsigned)((nthreads + 63) / 64)), block(64);
-        const size_t lds = (size_t)(nq * nq + nq * npt) * sizeof(double);
-        // The quadratic form's tile lives in dynamic LDS: (nq^2 + nq npt) doubles = 117 KB at n_ep = 64 (FULL_3D), above the 64 KB
-        // a kernel may use without asking.  Ask (gfx950 has 160 KB per CU); a device that refuses gets CM_ERR_UNSUPPORTED instead of
-        // a launch failure.
-        int dev = 0, lds_max = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) { (void)hipGetLastError(); lds_max = 65536; }
-        bool lds_ok = true;
+        const size_t lds = (size_t)(2 * nx * (npi + 2 * npj) + npi * 2 * nx + 4 * nx * nx) * sizeof(double);
         const bool found = dispatch<true>(m, [&]<int D, int Y, bool R, bool LS>() {
             if constexpr (!(MK == CM_SMALL_RATE_ELASTIC_PLASTIC && D == CM_UNIAXIAL_STRESS) && has_rate_dense<MK, Y>()) {
-                if (lds > 65536) {
-                    if (hipFuncSetAttribute((const void*)k_hessian_quadform_ep<nx_of<D, MK>()>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)lds) != hipSuccess) { (void)hipGetLastError(); lds_ok = false; return; }
-                } else if ((int64_t)lds > (int64_t)lds_max) { lds_ok = false; return; }
-                hipLaunchKernelGGL((k_hessian_weights_ep<D, CM_YIELD_ANY, kColdRot, MK>), grid, block, 0, s, md, B, K, n_ep, ep_index, gradu_hist,
-                                   xi_hist, lam_hist, sbar_hist, h, hss_hist, hxx_hist, W);
-                hipLaunchKernelGGL((k_hessian_quadform_ep<nx_of<D, MK>()>), dim3((unsigned)nps), dim3(256), lds, s, B, K, n_ep, W, dx_dp_hist,
-                                   dxe_hist, part);
+                hipLaunchKernelGGL((k_hessian_weights_blk<D, CM_YIELD_ANY, kColdRot, MK>), grid, block, 0, s, md, B, K, n_row, n_col,
+                                   sym ? 0 : n_row, sym, ep_cat, gradu_hist, xi_hist, lam_hist, sbar_hist, h, hss_hist, hxx_hist, W);
+                hipLaunchKernelGGL((k_hessian_qform_blk<nx_of<D, MK>()>), dim3((unsigned)nps), dim3(256), lds, s, B, K, n_row, n_col, W,
+                                   dx_dp_hist, dxe_row, dxe_col, part);
             }
         });
-        if (!found || !lds_ok) return CM_ERR_UNSUPPORTED;
+        if (!found) return CM_ERR_UNSUPPORTED;
         if (check_launch() != CM_OK) return CM_ERR_LAUNCH;
     }
-    cm_detail_sum_rows(s, part, nps, npt * npt, out);
+    cm_detail_sum_rows(s, part, nps, npi * npj, out);
     return check_launch();
 }
 
@@ -2350,7 +2376,7 @@ int cmi_objective_from_state(const cm_model_desc* m, int64_t B, const double* gr
 
 
 #if CM_HAS_PART(1) && !CM_HNN_VARIANT
-int cm_abi_version(void) { return 6; }
+int cm_abi_version(void) { return 7; }
 #endif
 
 #if CM_HAS_PART(1) && !CM_HNN_VARIANT
@@ -2499,6 +2525,13 @@ int64_t cm_hessian_ep_workspace_bytes(const cm_model_desc* m, int64_t B, int32_t
     const int64_t npt = CM_NUM_PARAMS + n_ep, nq = 2 * nx + npt, nps = (B > 0 ? B : 1) * (int64_t)K;
     return nps * (nq * nq + npt * npt) * (int64_t)sizeof(double);
 }
+int64_t cm_hessian_ep_block_workspace_bytes(const cm_model_desc* m, int64_t B, int32_t K, int32_t n_row, int32_t n_col) {
+    if (!m || B < 0 || K < 1 || n_row < 0 || n_col < 0) return CM_ERR_BAD_ARG;
+    const int nx = cm_num_xi(m);
+    if (nx < 0) return CM_ERR_UNSUPPORTED;
+    const int64_t npi = CM_NUM_PARAMS + n_row, npj = CM_NUM_PARAMS + n_col, nps = (B > 0 ? B : 1) * (int64_t)K;
+    return nps * ((2 * nx + npi) * (2 * nx + npj) + npi * npj) * (int64_t)sizeof(double) + (n_row + n_col) * (int64_t)sizeof(int32_t);
+}
 int64_t cm_hessian_workspace_bytes(const cm_model_desc* m, int64_t B, int32_t K) {
     if (!m || B < 0 || K < 1) return CM_ERR_BAD_ARG;
     const int nx = cm_num_xi(m);
@@ -2547,13 +2580,30 @@ int cm_hessian_history_ep(const cm_model_desc* m, int64_t B, int32_t K, int32_t 
                           const double* gradu_hist, const double* xi_hist, const double* lam_hist, const double* dxi_dp_hist,
                           const double* dxi_dpe_hist, const double* sigma_bar_hist, const double* hss6, const double* hss_hist,
                           const double* hxx_hist, double* hess, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!m) return CM_ERR_BAD_ARG;
+    if (!m || B < 0 || K < 1 || n_ep < 0) return CM_ERR_BAD_ARG;
+    const int64_t need = cm_hessian_ep_workspace_bytes(m, B, K, n_ep);
     if (m->model_kind == CM_SMALL_RATE_ELASTIC_PLASTIC)
-        return launch_hessian_history_ep<CM_SMALL_RATE_ELASTIC_PLASTIC>(m, B, K, n_ep, ep_index, gradu_hist, xi_hist, lam_hist, dxi_dp_hist,
-                                                                        dxi_dpe_hist, sigma_bar_hist, hss6, hss_hist, hxx_hist, hess, workspace,
-                                                                        workspace_bytes, stream);
-    return launch_hessian_history_ep<CM_SMALL_ELASTIC_PLASTIC>(m, B, K, n_ep, ep_index, gradu_hist, xi_hist, lam_hist, dxi_dp_hist, dxi_dpe_hist,
-                                                               sigma_bar_hist, hss6, hss_hist, hxx_hist, hess, workspace, workspace_bytes, stream);
+        return launch_hessian_block<CM_SMALL_RATE_ELASTIC_PLASTIC>(m, B, K, n_ep, ep_index, n_ep, ep_index, gradu_hist, xi_hist, lam_hist,
+                                                                   dxi_dp_hist, dxi_dpe_hist, dxi_dpe_hist, sigma_bar_hist, hss6, hss_hist,
+                                                                   hxx_hist, hess, workspace, workspace_bytes, need, stream);
+    return launch_hessian_block<CM_SMALL_ELASTIC_PLASTIC>(m, B, K, n_ep, ep_index, n_ep, ep_index, gradu_hist, xi_hist, lam_hist, dxi_dp_hist,
+                                                          dxi_dpe_hist, dxi_dpe_hist, sigma_bar_hist, hss6, hss_hist, hxx_hist, hess, workspace,
+                                                          workspace_bytes, need, stream);
+}
+int cm_hessian_history_ep_block(const cm_model_desc* m, int64_t B, int32_t K, int32_t n_row, const int32_t* row_ep, int32_t n_col,
+                                const int32_t* col_ep, const double* gradu_hist, const double* xi_hist, const double* lam_hist,
+                                const double* dxi_dp_hist, const double* dxe_row_hist, const double* dxe_col_hist, const double* sigma_bar_hist,
+                                const double* hss6, const double* hss_hist, const double* hxx_hist, double* hess, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    if (!m || B < 0 || K < 1 || n_row < 0 || n_col < 0) return CM_ERR_BAD_ARG;
+    const int64_t need = cm_hessian_ep_block_workspace_bytes(m, B, K, n_row, n_col);
+    if (m->model_kind == CM_SMALL_RATE_ELASTIC_PLASTIC)
+        return launch_hessian_block<CM_SMALL_RATE_ELASTIC_PLASTIC>(m, B, K, n_row, row_ep, n_col, col_ep, gradu_hist, xi_hist, lam_hist,
+                                                                   dxi_dp_hist, dxe_row_hist, dxe_col_hist, sigma_bar_hist, hss6, hss_hist,
+                                                                   hxx_hist, hess, workspace, workspace_bytes, need, stream);
+    return launch_hessian_block<CM_SMALL_ELASTIC_PLASTIC>(m, B, K, n_row, row_ep, n_col, col_ep, gradu_hist, xi_hist, lam_hist, dxi_dp_hist,
+                                                          dxe_row_hist, dxe_col_hist, sigma_bar_hist, hss6, hss_hist, hxx_hist, hess, workspace,
+                                                          workspace_bytes, need, stream);
 }
 #endif
 #if CM_HAS_PART(10)

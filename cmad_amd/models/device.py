@@ -814,7 +814,8 @@ class DeviceEvaluator:
         _lib.check(rc, "cm_hessian_history")
         return H
 
-    MAX_EXTENDED = 64          # kMaxEp in cmad_hip.hip: extended directions per second-order pass (the quadratic form's LDS tile)
+    MAX_EXTENDED = 64          # kMaxEp in cmad_hip.hip: extended directions per launch and side (the tile of the block quadratic form;
+                               # HistoryEngine tiles any number of leaves over it)
 
     def _check_extended(self, ep_index, what):
         if len(ep_index) > self.MAX_EXTENDED:
@@ -852,14 +853,52 @@ class DeviceEvaluator:
         if need < 0:
             _lib.check(int(need), "cm_hessian_ep_workspace_bytes")
         ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
-        hss = np.asarray(hss, dtype=np.float64)
-        h6 = (C.c_double * 6)(*[float(v) for v in hss]) if hss.ndim == 1 else None
-        hs_dev = None if hss.ndim == 1 else torch.from_numpy(np.ascontiguousarray(hss)).to(dev)
-        hx_dev = None if hxx is None else torch.from_numpy(np.ascontiguousarray(hxx, dtype=np.float64)).to(dev)
+        h6, hs_dev, hx_dev = self._curvatures(hss, hxx, dev)
         rc = self.L.cm_hessian_history_ep(C.byref(self.desc), B, K, ne, _ptr(ep), _ptr(gradu_hist), _ptr(xi_hist), _ptr(lam_hist),
                                           _ptr(dxi_dp_hist), _ptr(dxi_dpe_hist), _ptr(sigma_bar_hist), h6, _ptr(hs_dev), _ptr(hx_dev),
                                           _ptr(H), _ptr(ws), need, self._stream())
         _lib.check(rc, "cm_hessian_history_ep")
+        return H
+
+    @staticmethod
+    def _curvatures(hss, hxx, dev):
+        """The QoI curvatures as the second-order entries take them: (hss6 host array or None, hss_hist device or None,
+        hxx_hist device or None)."""
+        torch = _torch()
+        hss = np.asarray(hss, dtype=np.float64)
+        h6 = (C.c_double * 6)(*[float(v) for v in hss]) if hss.ndim == 1 else None
+        hs_dev = None if hss.ndim == 1 else torch.from_numpy(np.ascontiguousarray(hss)).to(dev)
+        hx_dev = None if hxx is None else torch.from_numpy(np.ascontiguousarray(hxx, dtype=np.float64)).to(dev)
+        return h6, hs_dev, hx_dev
+
+    def hessian_history_ep_block(self, row_ep, col_ep, gradu_hist, xi_hist, lam_hist, dxi_dp_hist, dxe_row_hist, dxe_col_hist,
+                                 sigma_bar_hist, hss, hxx=None):
+        """`cm_hessian_history_ep_block`: the (12 + n_row, 12 + n_col) block d2J/d[p, pe_row] d[p, pe_col] as a device tensor,
+        native parameters first on either side (KP order), then the leaves in list order.  Each side is one tile of at most
+        MAX_EXTENDED leaves; `dxe_row_hist` / `dxe_col_hist` are `direct_history_ep` of `row_ep` / `col_ep`.  The same list and
+        the same sensitivity tensor on both sides give `hessian_history_ep`'s result."""
+        self._check_extended(row_ep, "cm_hessian_history_ep_block")
+        self._check_extended(col_ep, "cm_hessian_history_ep_block")
+        torch = _torch()
+        K, B = gradu_hist.shape[0] - 1, gradu_hist.shape[2]
+        row, col = [int(e) for e in row_ep], [int(e) for e in col_ep]
+        for t, n, name in ((dxe_row_hist, len(row), "dxe_row_hist"), (dxe_col_hist, len(col), "dxe_col_hist")):
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (K + 1, self.nx, n, B)):
+                raise ValueError(f"{name}: expected a contiguous float64 CUDA tensor of shape ({K + 1}, {self.nx}, {n}, {B})")
+        dev = gradu_hist.device
+        ep_r = torch.tensor(row, dtype=torch.int32, device=dev)
+        # one list for both sides when they are one: the kernels then evaluate the symmetric weights once per pair
+        ep_c = ep_r if (row == col and dxe_row_hist is dxe_col_hist) else torch.tensor(col, dtype=torch.int32, device=dev)
+        H = torch.empty((_lib.CM_NUM_PARAMS + len(row), _lib.CM_NUM_PARAMS + len(col)), dtype=torch.float64, device=dev)
+        need = self.L.cm_hessian_ep_block_workspace_bytes(C.byref(self.desc), B, K, len(row), len(col))
+        if need < 0:
+            _lib.check(int(need), "cm_hessian_ep_block_workspace_bytes")
+        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        h6, hs_dev, hx_dev = self._curvatures(hss, hxx, dev)
+        rc = self.L.cm_hessian_history_ep_block(C.byref(self.desc), B, K, len(row), _ptr(ep_r), len(col), _ptr(ep_c), _ptr(gradu_hist),
+                                                _ptr(xi_hist), _ptr(lam_hist), _ptr(dxi_dp_hist), _ptr(dxe_row_hist), _ptr(dxe_col_hist),
+                                                _ptr(sigma_bar_hist), h6, _ptr(hs_dev), _ptr(hx_dev), _ptr(H), _ptr(ws), need, self._stream())
+        _lib.check(rc, "cm_hessian_history_ep_block")
         return H
 
     def param_blocks(self, ep_index, gradu, xi_prev, xi, gradu_prev=None):

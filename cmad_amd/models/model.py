@@ -98,7 +98,7 @@ class Model(ABC):
     def active_hessian_from_kp(self, H_kp, g_kp, info=None, ext=None):
         """Kernel-order Hessian + gradient (12,) -> Hessian w.r.t. the NATIVE active parameters: the chain rule through the
         elastic-constant map (lambda, mu)(E, nu, ...) adds sum_kp g_kp d2 kp / dp_i dp_j.  With `ext` = `extended_active()`
-        the Hessian is (12 + n_ext)^2 (cm_hessian_history_ep: native parameters first, then the extended leaves in `ext`
+        the Hessian is (12 + n_ext)^2 (HistoryEngine.hessian_ep: native parameters first, then the extended leaves in `ext`
         order); each extended leaf IS an active parameter (identity column)."""
         info = info or self._desc()[1]
         ext = ext or []

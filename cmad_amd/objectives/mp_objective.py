@@ -11,8 +11,9 @@ objective here is a fixed, small number of launches over the WHOLE history (`Mod
     MPDirectObjective         2 launches      cm_update_history -> qoi.history_cotangents -> cm_direct_history
     MPDirectAdjointObjective  4 launches      cm_update_history, cm_adjoint_history (keeps lam_k), cm_direct_history
                                               (keeps dxi_k/dp), cm_hessian_history (sum_k D_k^T W_k D_k); with active leaves
-                                              outside the 12 native parameters: + cm_param_adjoint_history, cm_direct_history_ep,
-                                              and cm_hessian_history_ep in place of cm_hessian_history
+                                              outside the 12 native parameters, any number of them: + cm_param_adjoint_history,
+                                              cm_direct_history_ep per tile of at most 64 leaves, and cm_hessian_history_ep_block
+                                              per pair of tiles in place of cm_hessian_history (HistoryEngine assembles the blocks)
 
 The QoI differentiates only its own formula (dJ/dsigma, explicit dJ/dxi, diagonal curvature in sigma); the model
 derivatives, the recursions over the steps and the reductions happen in the kernels.  Sensitivities leave the kernels

@@ -168,7 +168,7 @@ typedef struct cm_model_desc {
 } cm_model_desc;
 
 /* library / build info */
-int  cm_abi_version(void);                       /* 6: cm_update_ws / cm_update_tangent_ws / cm_update_workspace_bytes, cm_workspace_bytes includes the screened update's share; 5: cm_model_desc.ls_kind (CM_LS_LEGACY), hnn_width / hnn_offset (network hardening); cm_hessian_history takes per-step stress curvature and
+int  cm_abi_version(void);                       /* 7: cm_hessian_history_ep_block / cm_hessian_ep_block_workspace_bytes; 6: cm_update_ws / cm_update_tangent_ws / cm_update_workspace_bytes, cm_workspace_bytes includes the screened update's share; 5: cm_model_desc.ls_kind (CM_LS_LEGACY), hnn_width / hnn_offset (network hardening); cm_hessian_history takes per-step stress curvature and
                                                   * a state curvature; nn_weights layout carries the per-unit records */
 const char* cm_last_hip_error(void);             /* name of the last HIP error behind a CM_ERR_LAUNCH */
 int  cm_sizeof_model_desc(void);                 /* sizeof(cm_model_desc) as compiled, for binding checks */
@@ -494,16 +494,32 @@ int cm_hessian_history(const cm_model_desc* m, int64_t B, int32_t K,
  * cm_hessian_history_ep: cm_hessian_history over q = [xi_k, xi_{k-1}, p (12), pe (n_ep)]:
  *   hess[(12 + n_ep)^2] row-major, native parameters first (KP order), then the extended ones in ep_index order;
  *   n_ep = 0 reproduces cm_hessian_history.  ep_index: DEVICE int32[n_ep], n_ep <= 64.
- *   workspace: cm_hessian_ep_workspace_bytes(m, B, K, n_ep).
- * Total form: every deformation type; rate form: FULL_3D / PLANE_STRESS.
+ *   workspace: cm_hessian_ep_workspace_bytes(m, B, K, n_ep).  It is cm_hessian_history_ep_block with row list = column list.
+ * cm_hessian_history_ep_block: one rectangular block of the same Hessian, so that any number of extended leaves is covered by
+ *   tiles of at most 64 (the caller splits its leaves into tiles, takes cm_direct_history_ep per tile, one block per pair of
+ *   tiles, and the remaining blocks by transposition):
+ *   hess[(12 + n_row) * (12 + n_col)] row-major = d2J / d[p, pe_row] d[p, pe_col]: rows are the native parameters (KP order),
+ *   then row_ep in list order; columns the native parameters, then col_ep in list order.  row_ep / col_ep: DEVICE
+ *   int32[n_row] / int32[n_col], each count <= 64 (CM_ERR_BAD_ARG above); the lists may overlap or be equal.
+ *   dxe_row_hist / dxe_col_hist: cm_direct_history_ep of row_ep / col_ep.  With row_ep == col_ep and dxe_row_hist ==
+ *   dxe_col_hist (same pointers) the block is cm_hessian_history_ep's.
+ *   workspace: cm_hessian_ep_block_workspace_bytes(m, B, K, n_row, n_col), bounded by the 64 x 64 tile whatever the total count.
+ *   The sum over points and steps runs in a fixed order: the same inputs give the same bits.
+ * Total form: every deformation type; rate form: FULL_3D / PLANE_STRESS (both entries).
  */
 int64_t cm_hessian_ep_workspace_bytes(const cm_model_desc* m, int64_t B, int32_t K, int32_t n_ep);
+int64_t cm_hessian_ep_block_workspace_bytes(const cm_model_desc* m, int64_t B, int32_t K, int32_t n_row, int32_t n_col);
 int cm_direct_history_ep(const cm_model_desc* m, int64_t B, int32_t K, int32_t n_ep, const int32_t* ep_index,
                          const double* gradu_hist, const double* xi_hist, double* dxi_dpe_hist, void* stream);
 int cm_hessian_history_ep(const cm_model_desc* m, int64_t B, int32_t K, int32_t n_ep, const int32_t* ep_index,
                           const double* gradu_hist, const double* xi_hist, const double* lam_hist, const double* dxi_dp_hist,
                           const double* dxi_dpe_hist, const double* sigma_bar_hist, const double* hss6, const double* hss_hist,
                           const double* hxx_hist, double* hess, void* workspace, int64_t workspace_bytes, void* stream);
+int cm_hessian_history_ep_block(const cm_model_desc* m, int64_t B, int32_t K, int32_t n_row, const int32_t* row_ep,
+                                int32_t n_col, const int32_t* col_ep, const double* gradu_hist, const double* xi_hist,
+                                const double* lam_hist, const double* dxi_dp_hist, const double* dxe_row_hist,
+                                const double* dxe_col_hist, const double* sigma_bar_hist, const double* hss6, const double* hss_hist,
+                                const double* hxx_hist, double* hess, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * Extended parameter sensitivities.  The hand-derived kernels differentiate w.r.t. the 12 native parameters of
