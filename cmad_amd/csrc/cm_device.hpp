@@ -1144,9 +1144,26 @@ CM_D HardF hardening_f(const cm_model_desc& m, float alpha) {
 
 // NN(s) of icnn_yield_term for a network [6, H, 1], VALUE only, hidden units in float (~34 instead of ~66 instructions per unit; a
 // float copy of the weights in the pack was measured and bought nothing -- the kernel is no longer bound by VALU issue):
-// what k_screen classifies with; a point whose yield function lands within the float evaluation's error band of zero is
-// re-evaluated in double there.  Constants (biases of the output, f(0), scalers) stay double.
-CM_D double icnn_value_f(const cm_model_desc& m, const double s[6]) {
+// what k_screen classifies with; a point whose yield function lands within `err` of zero is re-evaluated in double there.
+// Constants (biases of the output, f(0), scalers) stay double.
+//
+// err bounds |v - NN(s)| for the exact NN, from the same loop (u = 2^-24; first order in u):
+//   unit o: t = sum_i xs_i r_i from float-rounded xs and r and 6 rounded products / sums:  |dt| <= 8u T,  T = sum_i |xs_i r_i|;
+//     b = b_o rounded: u|b|, and g = sp(b + t) + sp(b - t) moves by at most 2 per unit of b, 1 per unit of t;
+//     a+- = b +- t rounded: u(|b| + T) each;
+//     sp(a) = max(a, 0) + log(1 + e^-|a|): the argument's scaling by a rounded log2(e) (2u), v_exp_f32 (1 ulp: u), 1 + e (u),
+//     v_log_f32 (1 ulp of a result below 1: u), the rounded ln 2 and its product (2u) and the add (u sp(a)):
+//     <= 7u + u sp(a), with sp(a) <= |a| + 1 <= |b| + T + 1.
+//     So g_o is off by at most u (8T + 2|b| + 2(|b| + T) + 2 (7 + |b| + T + 1)) <= 16u m_o,  m_o = T + |b| + 1,
+//     and g_o wz_o, with wz_o rounded and the product rounded (g_o <= 2 m_o), by at most 20u |wz_o| m_o.
+//   F = sum of H such terms, recursively: + (H - 1) u sum_o |wz_o g_o| <= 2(H - 1) u S,  S = sum_o |wz_o| m_o.
+//   So |dF| <= 2u (H + 9) S, and v = (F/2 + b1 - f(0) - out_min) / out_scale is off by at most u (H + 9) S / |out_scale|.
+// err is twice that, c u (H + k) S / (2 |out_scale|) with c = 4, k = 9: the factor 2 covers the second-order terms, S itself
+// being summed in float (relative (H + 6) u), the double-precision arithmetic around the loop and the double evaluation that
+// decides the points inside the band (~1e-16 relative).  S is accumulated in the same loop; an overflow makes v or err infinite or
+// NaN, and every comparison with them sends the point to the double evaluation.
+struct IcnnValueF { double v, err; };
+CM_D IcnnValueF icnn_value_f(const cm_model_desc& m, const double s[6]) {
     const int H = m.nn_widths[1];
     const cm_uniform_ptr u = uniform_ptr(m.nn_weights);
     const cm_uniform_ptr sc = u + icnn_off_scalers(H);
@@ -1156,19 +1173,26 @@ CM_D double icnn_value_f(const cm_model_desc& m, const double s[6]) {
     float xs[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) xs[i] = (float)(sc[i] * x[i] + sc[6 + i]);
-    float F = 0.0f;
+    float F = 0.0f, S = 0.0f;
     for (int o = 0; o < H; ++o) {
         const cm_uniform_ptr r = rec + kIcnnRec * o;
-        float t = 0.0f;
+        float t = 0.0f, T = 1.0f;                               // T: 1 + sum_i |xs_i r_i|
 #pragma unroll
-        for (int i = 0; i < 6; ++i) t += xs[i] * (float)r[i];
+        for (int i = 0; i < 6; ++i) {
+            const float ri = (float)r[i];
+            t += xs[i] * ri;
+            T += fabsf(xs[i]) * fabsf(ri);
+        }
         const float b = (float)r[6], wz = (float)r[7];
         const float ap = b + t, an = b - t;
         const float spp = fmaxf(ap, 0.0f) + log_f(1.0f + exp_f(-fabsf(ap)));
         const float spn = fmaxf(an, 0.0f) + log_f(1.0f + exp_f(-fabsf(an)));
         F += (spp + spn) * wz;
+        S += (T + fabsf(b)) * fabsf(wz);
     }
-    return (0.5 * (double)F + u[icnn_off_b1(H)] - sc[14] - sc[13]) / sc[12];
+    const double ios = 1.0 / fabs(sc[12]);
+    constexpr double u24 = 0x1p-24;
+    return IcnnValueF{(0.5 * (double)F + u[icnn_off_b1(H)] - sc[14] - sc[13]) / sc[12], 2.0 * u24 * (double)(H + 9) * (double)S * ios};
 }
 
 // Cel a = 2 mu a + lambda (a0+a3+a5) d

@@ -508,15 +508,17 @@ __global__ __launch_bounds__(kScreenBlock) void k_screen(cm_model_desc m, int64_
     const double YH = m.Y + hardening(m, xp[6]).H;
     bool exact = true;
     if constexpr (YK == CM_YIELD_HYBRID_HILL_NN) {
-        // One hidden layer: the network term in float first (icnn_value_f: a third of this kernel's instructions less).  Its
-        // error is ~1e-6 of the terms it sums; a point within 2e-4 of (|phi_hill| + |N| + Y + H) of the surface -- one in a few
-        // thousand -- sends its wavefront through the double evaluation, which then decides for every lane.
+        // One hidden layer: the network term in float first (icnn_value_f: a third of this kernel's instructions less), with a
+        // bound on its error (cm_device.hpp).  A point whose phi - YH is within that bound of the elastic / plastic boundary below
+        // (phi - YH = -yield_tol / half_over_mu) sends its wavefront through the double evaluation, which then decides for every
+        // lane; outside the band the float decision is the double one, so no lane's result depends on its wave-mates.
         if (m.nn_nlayers == 3) {                                  // uniform
             double ph;
             yield_eval_p<CM_YIELD_HILL, false>(m, s, ph, gt, Hd);
-            const double nf = icnn_value_f(m, s);
-            phi = ph + nf;
-            const bool sure = fabs(phi - YH) > 2e-4 * (fabs(ph) + fabs(nf) + YH);      // (false for a NaN)
+            const IcnnValueF nf = icnn_value_f(m, s);
+            phi = ph + nf.v;
+            const double tol = fabs(m.yield_tol) / half_over_mu(m);
+            const bool sure = fabs(phi - YH) > nf.err + tol;       // (false for a NaN or an infinite bound)
             exact = __any(valid && !sure);
         }
     }

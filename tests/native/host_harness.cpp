@@ -675,6 +675,12 @@ void hh_log_pos(int64_t n, const double* x, double* y) { for (int64_t i = 0; i <
 void hh_icnn_symmetric(const double* w, int H, int64_t n, const double* xs, double* F, double* G, double* Hx) {
     for (int64_t i = 0; i < n; ++i) icnn_symmetric<true>(w, H, xs + 6 * i, F[i], G + 6 * i, Hx + 21 * i);
 }
+// cm::icnn_value_f (k_screen's float evaluation of the network term) on n material-frame stresses s6[n][6]: the value nf[n] and
+// the bound on its error that k_screen trusts, band[n] (k_screen widens it by yield_tol / half_over_mu, the shift of the
+// elastic / plastic boundary).  Only for one hidden layer, as in k_screen.
+void hh_icnn_value_f(const cm_model_desc* m, int64_t n, const double* s6, double* nf, double* band) {
+    for (int64_t i = 0; i < n; ++i) { const IcnnValueF v = icnn_value_f(*m, s6 + 6 * i); nf[i] = v.v; band[i] = v.err; }
+}
 void hh_soft_unit(int64_t n, const double* x, double* sp, double* sg) {
     for (int64_t i = 0; i < n; ++i) { const SoftUnit u = soft_unit(x[i]); sp[i] = u.sp; sg[i] = u.sg; }
 }
